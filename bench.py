@@ -76,7 +76,12 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget (0 disables)")
     ap.add_argument("--extras", type=int, default=1, help="also time C2, C3, the float32 mode and the kNN-30 kernel (N = 1)")
     ap.add_argument("--dry-run", action="store_true", help="orchestration only: gloo + CPU tensors + a stub launch")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; float32 / float64, at most 64 MB)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
 
 
 def launch_ranks(args):
@@ -201,6 +206,8 @@ def run_rank(args, world):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     full = gather.latest() if args.steps + args.warmup > 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, full, out)
     if world > 1:
         # what the one number above hides: every rank's own compute time per step (events on its launch stream around
         # its f4l_patch_loop: the LPT balance), its points and patches, and the all-gather by itself -- timed AFTER the metric's
@@ -318,6 +325,31 @@ class Problem:
         h = lambda t: t.cpu().numpy()  # noqa: E731
         return dict(src=h(d["src"][:s1]), src_off=h(d["src_off"][:p_hi + 1]), tgt=h(d["tgt"][:t1]), tgt_off=h(d["tgt_off"][:p_hi + 1]),
                     cs=h(self.cs[:c1]), ct=h(self.ct[:c1]), coff=h(self.coff[:p_hi + 1]))
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(torch, path, per_patch, out):
+    """What a caller of the timed path receives from its last step, as .npy files that two builds can be compared by: the
+    per-patch results of every patch in global patch order (T, fitness, rmse, iters; the all-gathered ones, so the same at
+    every --gpus) and a fixed, seeded sample of rank 0's displacement rows [s, T s] with the row indices it took.  The full
+    rows (24 B per source point) would not fit the 64 MB budget."""
+    import numpy as np
+    host = {k: per_patch[k].cpu().numpy().astype(np.float64) for k in ("T", "fitness", "rmse", "iters")}
+    left = DUMP_BYTES - sum(a.nbytes for a in host.values())
+    if left < 0:
+        raise SystemExit(f"bench.py: the per-patch results alone exceed the {DUMP_BYTES >> 20} MB of --dump-outputs")
+    rows = out.get("rows")
+    if rows is not None:
+        n = rows.shape[0]
+        m = min(n, 1 << 20, left // (6 * 4 + 8))  # float32 row + float64 index per sampled row
+        idx = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        host["rows_sample"] = rows[torch.from_numpy(idx).to(rows.device)].cpu().numpy()
+        host["rows_sample_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kernel_source_hash(which):

@@ -10,7 +10,7 @@
 // Mapping to CDNA4
 //   * one workgroup of NW waves (1, 2 or 4) per patch pair, every iteration inside the kernel.  The host sizes the LDS
 //     for the largest patch of a launch; batches of uneven sizes are binned on the device and launched per size class,
-//     side by side on helper streams (icp_launch_host);
+//     side by side on helper streams (icp_launch_host; one after the other, unbinned, on a stream under graph capture);
 //   * the target patch is counting-sorted ONCE into an LDS-resident uniform grid (patch_grid.h: cells of the search
 //     radius, finer for patches that are dense relative to it) and stays there for every iteration;
 //   * a pass has two phases.  Phase 1 re-measures every source point's previous correspondence and certifies it
@@ -112,6 +112,9 @@ struct IcpArgs {
     // size-class launches (icp_launch_host): workgroup b handles patch list[b] if b < *list_cnt, else nothing
     const int *list, *list_cnt;
     int prof_max_n;  // profiling builds: only patches up to this size are counted
+    // ... or, without a list (cls_hi > 0; the form a stream under graph capture gets), patch b if cls_lo < max(sources,
+    // targets) <= cls_hi, else nothing
+    int64_t cls_lo, cls_hi;
 };
 
 #ifdef F4L_ICP_PROF
@@ -401,6 +404,10 @@ __global__ __launch_bounds__(NW * 64, WIDE ? (MODE == F4L_ICP_POINT2POINT ? ICP_
     const int seg = ((a.cert_cap + NT - 1) / NT) * 64;  // queue entries one wave can produce
     unsigned short *queue = prev + ((a.cert_cap + 7) & ~7);
 
+    if (__builtin_expect(a.cls_hi > 0, 0) && !a.list && (int64_t)blockIdx.x < a.P) {
+        const int64_t b = blockIdx.x, ns = a.src_off[b + 1] - a.src_off[b], nt = a.tgt_off[b + 1] - a.tgt_off[b];
+        if ((ns > nt ? ns : nt) <= a.cls_lo || (ns > nt ? ns : nt) > a.cls_hi) return;
+    }
     int64_t p = blockIdx.x;
     if (a.list) {
         if ((int)blockIdx.x >= *a.list_cnt) return;
@@ -1454,6 +1461,7 @@ static int f4l::icp_launch_host(const float *src, const int64_t *src_off, const 
     const size_t lds = pl.lds;
     a.tgt_cap = tgt_cap; a.cert_cap = cert_cap; a.cell_cap = cell_cap; a.src_cap = src_cap; a.pp_cap = pl.pp_cap;
     a.list = nullptr; a.list_cnt = nullptr;
+    a.cls_lo = a.cls_hi = 0;
     a.prof = nullptr;
 #ifdef F4L_ICP_PROF
     if (getenv("F4L_ICP_PROF")) {
@@ -1563,6 +1571,29 @@ static int f4l::icp_launch_host(const float *src, const int64_t *src_off, const 
         cb.bound[cb.n++] = 0x7fffffff;
     }
     hipStream_t st = (hipStream_t)stream;
+    // A stream under graph capture gets the classes as kernel launches only, one after the other on the caller's stream: no
+    // binning buffer (each workgroup of a class launch keeps its patch only if the patch is of that class, the rule of
+    // icp_bin_patches), no helper streams, no events.  A captured launch whose graph also held the stream-ordered allocation,
+    // the memset and the fork / join through events crashed inside hipGraphLaunch at replay.  Same plans, same patches:
+    // the same results as the binned launches.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    if (cap != hipStreamCaptureStatusNone) {
+        for (int k = cb.n - 1; k >= 0; --k) {
+            const int64_t ms = max_src_patch_host < cb.bound[k] ? max_src_patch_host : cb.bound[k];
+            const int64_t mt = max_tgt_patch_host < cb.bound[k] ? max_tgt_patch_host : cb.bound[k];
+            const IcpPlan pk = icp_plan(ms, mt, f64, mode, throughput, rows_ok && k != overflow_class);
+            IcpArgs ak = a;
+            ak.tgt_cap = pk.tgt_cap; ak.cert_cap = pk.cert_cap; ak.cell_cap = pk.cell_cap; ak.src_cap = pk.src_cap; ak.pp_cap = pk.pp_cap;
+            ak.cls_lo = k > 0 ? cb.bound[k - 1] : -1;
+            ak.cls_hi = k < cb.n - 1 ? cb.bound[k] : INT64_MAX;  // (the last class takes whatever is larger, as in the binning)
+            const int rc = pk.rows_lp ? (f64 ? launch_rows<double>(ak, pk.rows_lp, st) : launch_rows<float>(ak, pk.rows_lp, st))
+                                      : (f64 ? launch_icp<double>(ak, mode, pk.nw, pk.lds, st, pk.wide)
+                                             : launch_icp<float>(ak, mode, pk.nw, pk.lds, st, pk.wide));
+            if (rc != F4L_OK) return rc;
+        }
+        return F4L_OK;
+    }
     int *buf = nullptr;
     const size_t buf_bytes = ((size_t)cb.n * (size_t)P + (size_t)cb.n) * sizeof(int);
     // One exit for every outcome (`fail` records the HIP error and jumps there): whatever was launched on a helper stream is

@@ -168,7 +168,14 @@ __global__ __launch_bounds__(ROWS_WAVES * 64, ROWS_WPE) void icp_rows_kernel(Icp
     const int64_t slot = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * PW + g;
     int64_t p = -1;
     if (a.list) { if (slot < (int64_t)*a.list_cnt) p = a.list[slot]; }
-    else if (slot < a.P) p = slot;
+    else if (slot < a.P) {
+        p = slot;
+        if (a.cls_hi > 0) {  // (size-class launch without a list: only the patches of this class)
+            const int64_t ns = a.src_off[p + 1] - a.src_off[p], nt = a.tgt_off[p + 1] - a.tgt_off[p];
+            const int64_t m = ns > nt ? ns : nt;
+            if (m <= a.cls_lo || m > a.cls_hi) p = -1;
+        }
+    }
     // A patch beyond the kernel's capacity is never loaded (its targets would overwrite the next patch's LDS) and is flagged
     // iters = -3; icp_launch_host only sends patches icp_bin_patches measured against ROWS_PPL * LP, so this guards other callers.
     bool oversize = false;

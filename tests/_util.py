@@ -107,3 +107,25 @@ def bits_checksum(a):
     """Order-dependent 64-bit checksum of an array's bytes (sum of the 32-bit words times their 1-based position, mod 2^64)."""
     w = np.frombuffer(np.ascontiguousarray(a).tobytes(), dtype=np.uint32).astype(np.uint64)
     return int((w * (np.arange(1, len(w) + 1, dtype=np.uint64) | np.uint64(1))).sum(dtype=np.uint64))
+
+
+# ---- the inputs of tests/golden/o3d_icp_golden.npz (tools/dump_o3d_goldens.py) --------------------------------------------------
+O3D_GOLDEN_THRESHOLD = 0.1
+
+
+def o3d_golden_cases():
+    """The fixture's clouds regenerated from their seed: a list of (src, tgt, init), float64 arrays holding float32 values (the
+    reference's clouds are float32, utils/o3d_tools.py:241-257).  One pair of surface patches per case; the source is the target's
+    surface moved by a small rotation and shift, the target carries noise."""
+    rng = np.random.default_rng(2024)
+    cases = []
+    for n_tgt, n_src, angle, shift, noise in [(900, 600, 0.004, 0.02, 0.002), (2500, 2000, 0.01, 0.03, 0.005),
+                                              (300, 40, 0.002, 0.01, 0.0), (5000, 4000, 0.006, 0.05, 0.003)]:
+        xy = rng.uniform(0, 2.0, (n_tgt, 2))
+        surf = lambda q: 0.25 * np.sin(2.1 * q[:, 0]) * np.cos(1.7 * q[:, 1]) + 0.05 * np.sin(9 * q[:, 0] + 1) * np.sin(7 * q[:, 1])  # noqa: E731
+        tgt = np.c_[xy, surf(xy) + rng.normal(0, noise, n_tgt)]
+        xy2 = rng.uniform(0.15, 1.85, (n_src, 2))
+        R0 = rot_from_axis_angle(rng.normal(size=3), angle)
+        src = np.c_[xy2, surf(xy2)] @ R0.T + rng.uniform(-shift, shift, 3)
+        cases.append((src.astype(np.float32).astype(np.float64), tgt.astype(np.float32).astype(np.float64), np.eye(4)))
+    return cases

@@ -14,7 +14,7 @@ import pytest
 from scipy.spatial import cKDTree
 
 from oracle import oracle as O
-from _util import rot_from_axis_angle
+from _util import O3D_GOLDEN_THRESHOLD, o3d_golden_cases, rot_from_axis_angle
 
 
 def _relief(xy):
@@ -438,30 +438,43 @@ def test_icp_oracle_edge_cases_and_batch_equals_single_calls():
 
 
 def test_icp_oracle_vs_open3d_goldens_when_present(golden_dir):
-    """tools/dump_o3d_goldens.py, run where Open3D 0.19.0 is installed, writes tests/golden/o3d_icp_golden.npz; with it
-    the oracle is pinned against the reference's actual arithmetic.  Absent here: skipped (parity unpinned)."""
+    """The cases of tools/dump_o3d_goldens.py (regenerated from its seed, _util.o3d_golden_cases) through the oracle's
+    point-to-point, point-to-plane and generalized ICP (epsilon 0 and Open3D's default): always against the numpy / scipy
+    restatements above, the same trajectory; and where tests/golden/o3d_icp_golden.npz exists (Open3D 0.19.0 writes it; it is
+    not installable where this suite normally runs) against Open3D's own results, which pins the oracle to the reference's
+    actual arithmetic."""
+    cases, thr = o3d_golden_cases(), O3D_GOLDEN_THRESHOLD
+    runs = {}
+    for c, (src, tgt, init) in enumerate(cases):
+        for icp_type in ("point2point", "point2plane"):
+            out = O.icp(src, tgt, init, max_corr_dist=thr, max_iter=30, icp_type=icp_type)
+            T, fit, rmse, iters, _, _ = _np_icp(src, tgt, init, thr, 30, icp_type,
+                                                O.o3d_estimate_normals(tgt, 30) if icp_type == "point2plane" else None)
+            assert out["iters"] == iters and out["fitness"] == fit, (c, icp_type)
+            assert np.abs(out["est_transform"] - T).max() <= 1e-9 and abs(out["inlier_rmse"] - rmse) <= 1e-12, (c, icp_type)
+            runs[icp_type, c] = out
+        sn, tn = O.o3d_estimate_normals(src, 30), O.o3d_estimate_normals(tgt, 30)
+        for tag, eps in (("generalized_icp", 0.0), ("generalized_icp_default", 1e-3)):
+            out = O.gicp(src, tgt, init, max_corr_dist=thr, max_iter=30, epsilon=eps)
+            T, fit, rmse, iters = _np_gicp(src, tgt, sn, tn, eps, thr, 30, T0=init)
+            assert out["iters"] == iters and out["fitness"] == fit, (c, tag)
+            assert np.abs(out["est_transform"] - T).max() < 1e-10 and abs(out["inlier_rmse"] - rmse) < 1e-12, (c, tag)
+            runs[tag, c] = out
     path = os.path.join(golden_dir, "o3d_icp_golden.npz")
     if not os.path.exists(path):
-        pytest.skip("no Open3D fixtures (tools/dump_o3d_goldens.py needs Open3D 0.19.0)")
+        return
     g = np.load(path)
-    for c in range(int(g["n_cases"])):
-        src, tgt = g[f"src_{c}"], g[f"tgt_{c}"]
-        for icp_type in ("point2point", "point2plane"):
-            out = O.icp(src, tgt, g[f"init_{c}"], max_corr_dist=float(g["threshold"]), max_iter=30, icp_type=icp_type)
-            T = g[f"T_{icp_type}_{c}"]
-            moved_a = src @ out["est_transform"][:3, :3].T + out["est_transform"][:3, 3]
-            moved_b = src @ T[:3, :3].T + T[:3, 3]
-            assert np.abs(moved_a - moved_b).max() <= 1e-6, (c, icp_type)  # SURVEY.md 8d: reference prints %.6f
-            assert abs(out["fitness"] - float(g[f"fitness_{icp_type}_{c}"])) <= 1e-3
-            assert abs(out["inlier_rmse"] - float(g[f"rmse_{icp_type}_{c}"])) <= 1e-5
-        for tag in ("generalized_icp", "generalized_icp_default"):
-            if f"T_{tag}_{c}" not in g:  # (files written before the generalized estimator was dumped)
-                continue
-            if tag == "generalized_icp":
-                assert float(g[f"epsilon_{tag}"]) == 0.0  # what utils/o3d_tools.py:41's `(False)` is read as here
-            out = O.gicp(src, tgt, g[f"init_{c}"], max_corr_dist=float(g["threshold"]), max_iter=30, epsilon=float(g[f"epsilon_{tag}"]))
-            T = g[f"T_{tag}_{c}"]
-            moved_a = src @ out["est_transform"][:3, :3].T + out["est_transform"][:3, 3]
-            assert np.abs(moved_a - (src @ T[:3, :3].T + T[:3, 3])).max() <= 1e-6, (c, tag)
-            assert abs(out["fitness"] - float(g[f"fitness_{tag}_{c}"])) <= 1e-3
-            assert abs(out["inlier_rmse"] - float(g[f"rmse_{tag}_{c}"])) <= 1e-5
+    assert int(g["n_cases"]) == len(cases) and float(g["threshold"]) == thr
+    for (tag, c), out in runs.items():
+        src = cases[c][0]
+        assert all(np.array_equal(g[f"{k}_{c}"], cases[c][j]) for j, k in enumerate(("src", "tgt", "init"))), c
+        if f"T_{tag}_{c}" not in g:  # (files written before the generalized estimator was dumped)
+            continue
+        if tag.startswith("generalized"):
+            # what utils/o3d_tools.py:41's `(False)` is read as here, and Open3D's default
+            assert float(g[f"epsilon_{tag}"]) == (0.0 if tag == "generalized_icp" else 1e-3), tag
+        T = g[f"T_{tag}_{c}"]
+        moved_a = src @ out["est_transform"][:3, :3].T + out["est_transform"][:3, 3]
+        assert np.abs(moved_a - (src @ T[:3, :3].T + T[:3, 3])).max() <= 1e-6, (c, tag)  # SURVEY.md 8d: reference prints %.6f
+        assert abs(out["fitness"] - float(g[f"fitness_{tag}_{c}"])) <= 1e-3
+        assert abs(out["inlier_rmse"] - float(g[f"rmse_{tag}_{c}"])) <= 1e-5

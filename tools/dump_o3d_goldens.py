@@ -26,24 +26,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     import open3d as o3d
-    from _util import rot_from_axis_angle
+    from _util import O3D_GOLDEN_THRESHOLD, o3d_golden_cases
 
-    rng = np.random.default_rng(2024)
-    threshold = 0.1
+    threshold = O3D_GOLDEN_THRESHOLD
     out = dict(threshold=np.float64(threshold), open3d_version=np.array(o3d.__version__))
-    cases = []
-    for c, (n_tgt, n_src, angle, shift, noise) in enumerate([(900, 600, 0.004, 0.02, 0.002), (2500, 2000, 0.01, 0.03, 0.005),
-                                                             (300, 40, 0.002, 0.01, 0.0), (5000, 4000, 0.006, 0.05, 0.003)]):
-        xy = rng.uniform(0, 2.0, (n_tgt, 2))
-        surf = lambda q: 0.25 * np.sin(2.1 * q[:, 0]) * np.cos(1.7 * q[:, 1]) + 0.05 * np.sin(9 * q[:, 0] + 1) * np.sin(7 * q[:, 1])
-        tgt = np.c_[xy, surf(xy) + rng.normal(0, noise, n_tgt)]
-        xy2 = rng.uniform(0.15, 1.85, (n_src, 2))
-        R0 = rot_from_axis_angle(rng.normal(size=3), angle)
-        src = np.c_[xy2, surf(xy2)] @ R0.T + rng.uniform(-shift, shift, 3)
-        # float32 storage, like the reference's clouds (pcd2tensor, utils/o3d_tools.py:241-257)
-        src, tgt = src.astype(np.float32).astype(np.float64), tgt.astype(np.float32).astype(np.float64)
-        init = np.eye(4)
-        cases.append((src, tgt, init))
+    cases = o3d_golden_cases()  # (the GPU parity test regenerates the same inputs from the same seed)
+    for c, (src, tgt, init) in enumerate(cases):
         out[f"src_{c}"], out[f"tgt_{c}"], out[f"init_{c}"] = src, tgt, init
         for icp_type in ("point2point", "point2plane"):
             s, t = o3d.geometry.PointCloud(), o3d.geometry.PointCloud()
